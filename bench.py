@@ -9,7 +9,14 @@ HBM before the timed region.  With --gpus N (launched by torch.distributed.run)
 the 512^3 grid is z-slab decomposed over N ranks (strong scaling) with RCCL halo
 exchange + all-reduce of the Lanczos dot products.
 
-roofline: for the NLSE the dominant kernel is the fused tail k_tail<NLSE, m>
+A plain run (`--gpus 1 --steps N --warmup W`) sets up, warms up, times the N
+steps and prints the result line; --dump-outputs DIR also writes the field the
+last timed step left (a fixed seeded sample of it at the large grids) as
+DIR/<name>.npy, identical inputs from run to run.  --full adds what takes runs
+of its own: the per-kernel timing pass (roofline, step_roofline) and
+cpu_baseline with its full-grid parity check.
+
+roofline (--full): for the NLSE the dominant kernel is the fused tail k_tail<NLSE, m>
 (the last Lanczos vector + combination + both nonlinear half-steps; m-1 stored
 vectors read, the next start vector written, u on a call's last step: the most
 bytes per launch; the largest two-vector pass k_p2d<m-4> takes about as long at
@@ -18,7 +25,7 @@ two-vector pass; timed with HIP events on the
 solver's own stream in a separate pass of --prof-steps steps right after the
 timed region (the timed region itself carries no per-launch events).
 --gpus N without torch.distributed.run: bench.py starts the N ranks itself.
-cpu_baseline: the oracle (single-threaded C++ restatement of the reference's
+cpu_baseline (--full): the oracle (single-threaded C++ restatement of the reference's
 Eigen path, oracle/) on a bounded 128^3 sample of the same workload.
 """
 from __future__ import annotations
@@ -660,6 +667,139 @@ def selfcheck_main(args, dist, world, rank, local_rank):
     dist.barrier()
 
 
+# ---- --dump-outputs: the timed path's result, for comparing two builds output for output ----
+DUMP_MAX_CELLS = 1 << 21   # per array: 32 MiB of c128 as float64 pairs (64 MB in all allowed)
+DUMP_SEED = 20240229
+
+
+def dump_sample_index(cells_total):
+    """The global cell indices written by --dump-outputs: every cell of a field of up to
+    DUMP_MAX_CELLS cells, else a fixed (seeded, sorted) sample of about that many."""
+    if cells_total <= DUMP_MAX_CELLS:
+        return np.arange(cells_total, dtype=np.int64)
+    rng = np.random.default_rng(DUMP_SEED)
+    return np.unique(rng.integers(0, cells_total, DUMP_MAX_CELLS, dtype=np.int64))
+
+
+def as_real(a):
+    """float64 view for .npy: a complex field as (cells, 2) = (re, im)."""
+    a = np.ascontiguousarray(a)
+    return a.view(np.float64).reshape(-1, 2) if np.iscomplexobj(a) else a.astype(np.float64, copy=False)
+
+
+def dump_outputs(path, s, w, dt, dist, world, rank):
+    """Write what a caller reads back after the last timed step: the field u (get_field)
+    and, for the Gautschi equations, the velocity v (get_sg_velocity), each at the cells
+    of dump_sample_index, as float64 <path>/<name>.npy.  With N ranks every rank
+    contributes the sampled cells of its slab, in rank (= global index) order."""
+    dim, n = w["dim"], w["n"]
+    plane = n * n if dim == 3 else n
+    idx = dump_sample_index(n ** dim)
+    lo = s.z0 * plane
+    local = idx[(idx >= lo) & (idx < lo + s.n_local)] - lo
+    arrays = {"u": s.get_field()[local]}
+    if w["eq"] in (2, 4):
+        arrays["v"] = s.get_sg_velocity(dt)[local]
+    if world > 1:
+        arrays = {k: gather_slabs(v, dist, world, rank) for k, v in arrays.items()}
+    if rank == 0:
+        os.makedirs(path, exist_ok=True)
+        for name, a in arrays.items():
+            np.save(os.path.join(path, name + ".npy"), as_real(a))
+
+
+def roofline_report(args, w, m, n_local, world, tm, step_ms):
+    """--full: the "roofline" and "step_roofline" entries of the result line, from the
+    per-kernel times `tm` of the separate timing pass and the timed region's ms per step."""
+    # dominant kernel: the fused final pass k_final_fused<m> when the step uses it
+    # (NLSE, m >= 3: W_0..W_{m-2} read, u and the next W_0 written, + m(x) on G2),
+    # else the largest update pass k_update<J = m-2> (J+1 reads + 1 write); with
+    # the two-vector passes (update launches at even J only) the longer of the
+    # tail and the largest pass k_p2d<J> (J+1 reads + 2 writes)
+    esz = 8 if w["eq"] in (2, 4) else 16
+    fcnt = tm["class_count"].get("final", 0)
+    ucnt = tm["update_count"]
+    # s-step passes (k_p2d / k_p3d): update launches only at the schedule's pass
+    # starts J (never at J = 1); pass J writes S_{J+1} .. S_{J+ns}, the last one S_{m-2}
+    pass2 = m >= 4 and ucnt[0] > 0 and ucnt[1] == 0
+    sched = []
+    if pass2:
+        Js = [j for j in range(m - 1) if ucnt[j]]
+        sched = [(j, (Js[i + 1] if i + 1 < len(Js) else m - 2) - j) for i, j in enumerate(Js)]
+    pass_ms = {j: tm["update_ms"][j] / ucnt[j] for j, _ in sched}
+    p2J, p2ns = max(sched, key=lambda e: pass_ms[e[0]]) if sched else (0, 0)
+    p2_ms = pass_ms.get(p2J, 0.0)
+    tail_ms = tm["class_ms"]["final"] / fcnt if fcnt else 0.0
+    own_bytes = None
+    # the NLSE tail writes u = N(y) only on the last step of an nls_step call (the
+    # others write just the next start vector): one call per run() for the G1 NLSE
+    multi = w["eq"] in (0, 1) and not w.get("sewi")
+    u_frac = (1.0 / args.steps) if multi else 1.0           # timed region
+    u_frac_prof = (1.0 / max(1, args.prof_steps)) if multi else 1.0  # timing pass
+    own_bytes = moved_bytes_per_cell_step(w, m, sched, pass2, u_frac, tm, args.steps)
+    # the NLSE's dominant kernel is the fused tail (the most bytes per launch: m-1 reads,
+    # the next start vector and u; the largest pass takes about as long, so a timing
+    # rule would flip between runs), else the largest two-vector pass
+    nlse_tail = bool(fcnt) and w["eq"] in (0, 1, 3) and not w.get("sewi")
+    if pass2 and not nlse_tail:
+        J = p2J
+        cnt = ucnt[J]
+        avg_ms = p2_ms
+        bytes_launch = (J + 1 + p2ns) * esz * n_local
+        kname = f"k_p{max(p2ns, 2)}d<J={J}> ({p2ns}-vector Lanczos pass: radius-{p2ns} stencil + CGS " \
+                f"coefficients, {J + 1} reads + {p2ns} writes)"
+        kprefix = f"k_p{max(p2ns, 2)}d<{J}, "
+    elif fcnt and w["eq"] in (0, 1, 3) and not w.get("sewi"):
+        J = m - 2
+        cnt = fcnt
+        avg_ms = tm["class_ms"]["final"] / fcnt
+        bytes_launch = ((m + u_frac_prof) * esz + (8 if w["eq"] == 3 else 0)) * n_local
+        kname = f"k_tail<NLSE, M={m}> (fused tail: stencil + last Lanczos vector + combination " \
+                f"+ N(1/2) x2, {m - 1} reads + the next start vector + u on a call's last step)"
+        kprefix = "k_tail<"
+    else:  # the largest update pass that ran (m-3 where the basis ends in a fused tail)
+        J = max([j for j, c in enumerate(tm["update_count"]) if c] or [0])
+        cnt = tm["update_count"][J]
+        avg_ms = tm["update_ms"][J] / cnt if cnt else float("nan")
+        bytes_launch = (J + 2) * esz * n_local
+        kname = f"k_update<J={J}> (stencil + CGS + write, {J + 1} reads + 1 write)"
+        kprefix = None  # (no per-J PMC entry is matched for the one-vector passes)
+    achieved = bytes_launch / (avg_ms * 1e-3) / 1e9 if cnt else None
+    traffic = load_traffic(args.workload, m, kprefix) if world == 1 and kprefix else None
+    step_bytes = algorithmic_bytes_per_cell_step(m, w["eq"], w.get("sewi", False)) * n_local
+    return {
+        "roofline": {
+            "bound": "hbm",
+            "kernel": kname,
+            "achieved": achieved,
+            "peak": HBM_PEAK_GBS,
+            "unit": "GB/s",
+            "frac": (achieved / HBM_PEAK_GBS) if achieved else None,
+            "traffic": traffic,
+            "bytes_per_launch": bytes_launch,
+            "avg_launch_ms": avg_ms,
+            "timed_in": f"separate {max(1, args.prof_steps)}-step pass with HIP events (not the timed region)",
+        },
+        "step_roofline": {
+            # bytes per cell and step that THIS implementation moves (model of its
+            # passes, DESIGN.md section 3), and the rate they move at over the step
+            "moved_bytes_per_cell_step": own_bytes,
+            "moved_GBs": own_bytes * n_local / (step_ms * 1e-3) / 1e9 if own_bytes else None,
+            "frac": own_bytes * n_local / (step_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if own_bytes else None,
+            # the reference algorithm's bytes (SURVEY 8(d) E(m): one vector per Lanczos
+            # iteration, MGS re-reads): an equivalent rate, above the HBM peak once the
+            # passes move fewer bytes than that model -- not a bandwidth
+            "reference_model_bytes_per_cell_step": algorithmic_bytes_per_cell_step(m, w["eq"],
+                                                                                    w.get("sewi", False)),
+            "reference_model_equiv_GBs": step_bytes / (step_ms * 1e-3) / 1e9,
+            "gpu_kernel_ms_per_step": {k: v / max(tm["steps"], 1) for k, v in tm["class_ms"].items()},
+            "lanczos": ("s-step passes " + " ".join(f"J{j}:{ns}" for j, ns in sched) + " + fused tail")
+            if pass2 else "one-vector passes + fused tail",
+            "bases_per_step": 2 if w["eq"] in (2, 4) else (3 if w.get("sewi") else 1),
+        },
+    }
+
+
 def main():
     out = _claim_stdout()
     ap = argparse.ArgumentParser()
@@ -669,12 +809,17 @@ def main():
     ap.add_argument("--workload", default="nlse3d_512", choices=sorted(WORKLOADS))
     ap.add_argument("--n", type=int, default=None, help="override grid side (testing only)")
     ap.add_argument("--m", type=int, default=None, help="override Krylov dim (testing only)")
-    ap.add_argument("--cpu-steps", type=int, default=10)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step left (the field a caller reads back) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-kernel timing pass (roofline, step_roofline) and the CPU baseline with "
+                         "its full-grid parity check; a run without it only times the steps")
+    ap.add_argument("--cpu-steps", type=int, default=10, help="--full: steps of the CPU baseline's sample")
     ap.add_argument("--prof-steps", type=int, default=5,
-                    help="steps of the separate per-kernel timing pass (after the timed region)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="--full: steps of the separate per-kernel timing pass (after the timed region)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-full-grid-cpu", action="store_true",
-                    help="skip the one-step CPU oracle run at the full 512^3 grid")
+                    help="--full: skip the one-step CPU oracle run at the full 512^3 grid")
     ap.add_argument("--no-selfcheck", action="store_true",
                     help="N > 1: skip the multi-GPU self-check job (default exchange)")
     ap.add_argument("--selfcheck-json", default=None, help=argparse.SUPPRESS)  # the child job
@@ -742,7 +887,7 @@ def main():
         u /= np.sqrt(global_mass(u, dx ** dim, dist))  # nlse_call.cpp:41-49
         s.set_field(u)
     # the full-grid CPU baseline steps the same initial field (headline workload, 1 rank)
-    keep_u = world == 1 and not args.no_cpu_baseline and args.workload == "nlse3d_512" and not args.n
+    keep_u = args.full and world == 1 and not args.no_cpu_baseline and args.workload == "nlse3d_512" and not args.n
     u_full = u if keep_u else None
     del u
     dt = w["dt"]
@@ -775,75 +920,23 @@ def main():
         dist.barrier()
     el = time.perf_counter() - t0
     el = max_over_ranks(el, dist)
-    # per-kernel times (roofline) from a separate, untimed pass with HIP events
-    # around every launch on the solver's own streams
-    s.reset_timing()
-    s.set_timing(True)
-    run(max(1, args.prof_steps))
-    s.sync()
-    tm = s.timing()
-    s.set_timing(False)
     cells_total = n ** dim
     value = cells_total * args.steps / el / 1e6
-    n_local = s.n_local
-
-    # dominant kernel: the fused final pass k_final_fused<m> when the step uses it
-    # (NLSE, m >= 3: W_0..W_{m-2} read, u and the next W_0 written, + m(x) on G2),
-    # else the largest update pass k_update<J = m-2> (J+1 reads + 1 write); with
-    # the two-vector passes (update launches at even J only) the longer of the
-    # tail and the largest pass k_p2d<J> (J+1 reads + 2 writes)
-    esz = 8 if w["eq"] in (2, 4) else 16
-    fcnt = tm["class_count"].get("final", 0)
-    ucnt = tm["update_count"]
-    # s-step passes (k_p2d / k_p3d): update launches only at the schedule's pass
-    # starts J (never at J = 1); pass J writes S_{J+1} .. S_{J+ns}, the last one S_{m-2}
-    pass2 = m >= 4 and ucnt[0] > 0 and ucnt[1] == 0
-    sched = []
-    if pass2:
-        Js = [j for j in range(m - 1) if ucnt[j]]
-        sched = [(j, (Js[i + 1] if i + 1 < len(Js) else m - 2) - j) for i, j in enumerate(Js)]
-    pass_ms = {j: tm["update_ms"][j] / ucnt[j] for j, _ in sched}
-    p2J, p2ns = max(sched, key=lambda e: pass_ms[e[0]]) if sched else (0, 0)
-    p2_ms = pass_ms.get(p2J, 0.0)
-    tail_ms = tm["class_ms"]["final"] / fcnt if fcnt else 0.0
-    own_bytes = None
-    # the NLSE tail writes u = N(y) only on the last step of an nls_step call (the
-    # others write just the next start vector): one call per run() for the G1 NLSE
-    multi = w["eq"] in (0, 1) and not w.get("sewi")
-    u_frac = (1.0 / args.steps) if multi else 1.0           # timed region
-    u_frac_prof = (1.0 / max(1, args.prof_steps)) if multi else 1.0  # timing pass
-    own_bytes = moved_bytes_per_cell_step(w, m, sched, pass2, u_frac, tm, args.steps)
-    # the NLSE's dominant kernel is the fused tail (the most bytes per launch: m-1 reads,
-    # the next start vector and u; the largest pass takes about as long, so a timing
-    # rule would flip between runs), else the largest two-vector pass
-    nlse_tail = bool(fcnt) and w["eq"] in (0, 1, 3) and not w.get("sewi")
-    if pass2 and not nlse_tail:
-        J = p2J
-        cnt = ucnt[J]
-        avg_ms = p2_ms
-        bytes_launch = (J + 1 + p2ns) * esz * n_local
-        kname = f"k_p{max(p2ns, 2)}d<J={J}> ({p2ns}-vector Lanczos pass: radius-{p2ns} stencil + CGS " \
-                f"coefficients, {J + 1} reads + {p2ns} writes)"
-        kprefix = f"k_p{max(p2ns, 2)}d<{J}, "
-    elif fcnt and w["eq"] in (0, 1, 3) and not w.get("sewi"):
-        J = m - 2
-        cnt = fcnt
-        avg_ms = tm["class_ms"]["final"] / fcnt
-        bytes_launch = ((m + u_frac_prof) * esz + (8 if w["eq"] == 3 else 0)) * n_local
-        kname = f"k_tail<NLSE, M={m}> (fused tail: stencil + last Lanczos vector + combination " \
-                f"+ N(1/2) x2, {m - 1} reads + the next start vector + u on a call's last step)"
-        kprefix = "k_tail<"
-    else:  # the largest update pass that ran (m-3 where the basis ends in a fused tail)
-        J = max([j for j, c in enumerate(tm["update_count"]) if c] or [0])
-        cnt = tm["update_count"][J]
-        avg_ms = tm["update_ms"][J] / cnt if cnt else float("nan")
-        bytes_launch = (J + 2) * esz * n_local
-        kname = f"k_update<J={J}> (stencil + CGS + write, {J + 1} reads + 1 write)"
-        kprefix = None  # (no per-J PMC entry is matched for the one-vector passes)
-    achieved = bytes_launch / (avg_ms * 1e-3) / 1e9 if cnt else None
-    traffic = load_traffic(args.workload, m, kprefix) if world == 1 and kprefix else None
-    step_bytes = algorithmic_bytes_per_cell_step(m, w["eq"], w.get("sewi", False)) * n_local
     step_ms = el * 1e3 / args.steps
+    if args.dump_outputs:
+        # what a caller of the timed path holds after its last step (before the timing
+        # pass below moves the state on)
+        dump_outputs(args.dump_outputs, s, w, dt, dist, world, rank)
+    tm = None
+    if args.full:
+        # per-kernel times (roofline) from a separate, untimed pass with HIP events
+        # around every launch on the solver's own streams
+        s.reset_timing()
+        s.set_timing(True)
+        run(max(1, args.prof_steps))
+        s.sync()
+        tm = s.timing()
+        s.set_timing(False)
     result = {
         "metric": "Mcells*steps/s and achieved HBM GB/s, 3D NLSE 512^3 at 1/2/4/8 MI355X"
         if args.workload == "nlse3d_512" else f"Mcells*steps/s ({w['desc']})",
@@ -864,35 +957,6 @@ def main():
                    "parallelism": f"z-slab x{world}" if world > 1 else "single GPU",
                    "ranks": {"world": world, "transport": comm_transport,
                              "library_comm_ranks": comm_ranks, "slab_planes_rank0": int(s.nzl)}},
-        "roofline": {
-            "bound": "hbm",
-            "kernel": kname,
-            "achieved": achieved,
-            "peak": HBM_PEAK_GBS,
-            "unit": "GB/s",
-            "frac": (achieved / HBM_PEAK_GBS) if achieved else None,
-            "traffic": traffic,
-            "bytes_per_launch": bytes_launch,
-            "avg_launch_ms": avg_ms,
-            "timed_in": f"separate {max(1, args.prof_steps)}-step pass with HIP events (not the timed region)",
-        },
-        "step_roofline": {
-            # bytes per cell and step that THIS implementation moves (model of its
-            # passes), and the rate they move at over the step
-            "moved_bytes_per_cell_step": own_bytes,
-            "moved_GBs": own_bytes * n_local / (step_ms * 1e-3) / 1e9 if own_bytes else None,
-            "frac": own_bytes * n_local / (step_ms * 1e-3) / 1e9 / HBM_PEAK_GBS if own_bytes else None,
-            # the reference algorithm's bytes (one vector per Lanczos
-            # iteration, MGS re-reads): an equivalent rate, above the HBM peak once the
-            # passes move fewer bytes than that model -- not a bandwidth
-            "reference_model_bytes_per_cell_step": algorithmic_bytes_per_cell_step(m, w["eq"],
-                                                                                    w.get("sewi", False)),
-            "reference_model_equiv_GBs": step_bytes / (step_ms * 1e-3) / 1e9,
-            "gpu_kernel_ms_per_step": {k: v / max(tm["steps"], 1) for k, v in tm["class_ms"].items()},
-            "lanczos": ("s-step passes " + " ".join(f"J{j}:{ns}" for j, ns in sched) + " + fused tail")
-            if pass2 else "one-vector passes + fused tail",
-            "bases_per_step": 2 if w["eq"] in (2, 4) else (3 if w.get("sewi") else 1),
-        },
         # the basis allocation kept among the candidates probed at nls_create (DESIGN.md
         # section 4 "Placement"; candidates 0: no probe on this handle)
         "placement": placement,
@@ -900,6 +964,8 @@ def main():
         # beside it (a prebuilt libnls_amd.so that does not match them says so here)
         "build": _build_record(nls_amd),
     }
+    if args.full:
+        result.update(roofline_report(args, w, m, s.n_local, world, tm, step_ms))
     if world > 1:
         # the self-check job's report and the exchange this timed run used (peer_state of
         # this handle: "active" = peer stores, "off" = RCCL send/recv exchange)
@@ -912,7 +978,7 @@ def main():
         s.step(dt, 1)
         gpu_one = s.get_field()
     s.close()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(args, u_full, gpu_one)
     if rank == 0:
         print(json.dumps(result), file=out, flush=True)

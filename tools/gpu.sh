@@ -6,8 +6,8 @@
 #   suite          pytest -m gpu (one process)            -> suite.txt
 #   suite:EXPR     the same restricted to -k EXPR
 #   smoke          __graft_entry__.smoke()                 -> smoke.txt
-#   bench          python bench.py (headline, cpu baseline) -> bench_nlse3d_512.json
-#   bench:WL       python bench.py --workload WL            -> bench_WL.json
+#   bench          python bench.py --full (headline, roofline, cpu baseline) -> bench_nlse3d_512.json
+#   bench:WL       python bench.py --full --workload WL            -> bench_WL.json
 #   set            bench of every BASELINE workload + KG    -> bench_*_set.json
 #   prof[:WL]      bench under rocprofv3 --kernel-trace --stats -> prof_WL/, bench_WL_under_rocprof.json
 #   pmc[:WL]       FETCH_SIZE / WRITE_SIZE / TCC hit passes, one counter group per run -> pmc_WL/
@@ -55,21 +55,21 @@ for st in "$@"; do
       cat "$OUT/smoke.txt" ;;
     bench)
       if [ -n "$arg" ]; then
-        run 300 "$OUT/bench_$arg.json" python bench.py --workload "$arg" --no-cpu-baseline
+        run 300 "$OUT/bench_$arg.json" python bench.py --full --workload "$arg" --no-cpu-baseline
         cat "$OUT/bench_$arg.json"
       else
-        run 300 "$OUT/bench_nlse3d_512.json" python bench.py
+        run 300 "$OUT/bench_nlse3d_512.json" python bench.py --full
         cat "$OUT/bench_nlse3d_512.json"
       fi ;;
     set)
       for w in nlse2d_4096 sg2d_8192 g2_3d_256 kg_3d_256 cq3d_1024 nlse3d_512; do
-        run 300 "$OUT/bench_${w}_set.json" python bench.py --workload "$w" --steps 10 --warmup 2 --no-cpu-baseline
+        run 300 "$OUT/bench_${w}_set.json" python bench.py --full --workload "$w" --steps 10 --warmup 2 --no-cpu-baseline
         cat "$OUT/bench_${w}_set.json"
       done ;;
     prof)
       wl=${arg:-nlse3d_512}
       run 300 "$OUT/bench_${wl}_under_rocprof.json" rocprofv3 --kernel-trace --stats -d "$OUT/prof_$wl" -o run \
-        --output-format csv -- python3 bench.py --workload "$wl" --steps 10 --warmup 2 --no-cpu-baseline
+        --output-format csv -- python3 bench.py --full --workload "$wl" --steps 10 --warmup 2 --no-cpu-baseline
       # the bench's own dispatches (after the placement probe's; tools/trace_stats.py)
       f=$(ls "$OUT/prof_$wl"/*kernel_trace.csv 2>/dev/null | head -n 1)
       [ -n "$f" ] && python3 tools/trace_stats.py "$f" > "$OUT/prof_$wl/bench_kernel_stats.csv"
@@ -85,7 +85,7 @@ for st in "$@"; do
         # averages; the bytes a kernel moves do not depend on the placement,
         # profiles/r06/place_diag.txt), so the tails that write u stay 2 of 7
         NLS_PLACE=1 timeout -s KILL 200 rocprofv3 --pmc $grp --output-format csv -d "$OUT/pmc_$wl/p$i" -o run -- \
-          python3 bench.py --workload "$wl" --steps 2 --warmup 0 --no-cpu-baseline > "$OUT/pmc_$wl/p$i.log" 2>&1 || exit $?
+          python3 bench.py --full --workload "$wl" --steps 2 --warmup 0 --no-cpu-baseline > "$OUT/pmc_$wl/p$i.log" 2>&1 || exit $?
       done ;;
     sq)
       # issue / wait fractions and instruction counts per wave (8 SQ counters, one pass)
@@ -94,7 +94,7 @@ for st in "$@"; do
       echo "[gpu.sh] $(date +%T) sq $wl"
       NLS_PLACE=1 timeout -s KILL 200 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_ACTIVE_INST_ANY SQ_WAIT_ANY SQ_WAIT_INST_ANY \
         SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS --output-format csv -d "$OUT/sq_$wl/p1" -o run -- \
-        python3 bench.py --workload "$wl" --steps 2 --warmup 0 --no-cpu-baseline > "$OUT/sq_$wl/p1.log" 2>&1 || exit $?
+        python3 bench.py --full --workload "$wl" --steps 2 --warmup 0 --no-cpu-baseline > "$OUT/sq_$wl/p1.log" 2>&1 || exit $?
       python3 tools/pmc_table.py "$OUT/sq_$wl" > "$OUT/sq_$wl.txt" && cat "$OUT/sq_$wl.txt" ;;
     sq2)
       # LDS and instruction-wait detail (8 SQ counters, one pass)
@@ -103,7 +103,7 @@ for st in "$@"; do
       echo "[gpu.sh] $(date +%T) sq2 $wl"
       NLS_PLACE=1 timeout -s KILL 200 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS \
         SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_ANY --output-format csv -d "$OUT/sq2_$wl/p1" -o run -- \
-        python3 bench.py --workload "$wl" --steps 2 --warmup 0 --no-cpu-baseline > "$OUT/sq2_$wl/p1.log" 2>&1 || exit $?
+        python3 bench.py --full --workload "$wl" --steps 2 --warmup 0 --no-cpu-baseline > "$OUT/sq2_$wl/p1.log" 2>&1 || exit $?
       python3 tools/pmc_table.py "$OUT/sq2_$wl" > "$OUT/sq2_$wl.txt" && cat "$OUT/sq2_$wl.txt" ;;
     ab)
       # same-box A/B: every variant build nonlinear-solvers_amd/lib_v*/ against lib, two
@@ -113,7 +113,7 @@ for st in "$@"; do
       for rep in 1 2; do
         for v in $vars lib; do
           NLS_AMD_LIB=$PWD/nonlinear-solvers_amd/$v/libnls_amd.so run 300 "$OUT/ab_${wl}_${v}_$rep.json" \
-            python bench.py --workload "$wl" --steps 10 --warmup 2 --no-cpu-baseline
+            python bench.py --full --workload "$wl" --steps 10 --warmup 2 --no-cpu-baseline
           python3 -c "import json,sys; d=json.load(open(sys.argv[1])); r=d['roofline']; k=d['step_roofline']['gpu_kernel_ms_per_step']; \
 print(f\"$v rep$rep ms/step {d['ms_per_step']:.3f} value {d['value']:.1f} dominant {r['avg_launch_ms']:.4f} ms frac {r['frac']:.3f} \
 \" + ' '.join(f'{a}:{b:.3f}' for a, b in k.items()))" "$OUT/ab_${wl}_${v}_$rep.json" \
@@ -146,7 +146,7 @@ print(f\"$v rep$rep ms/step {d['ms_per_step']:.3f} value {d['value']:.1f} domina
         for ev in $(echo "$sets" | tr ',' ' '); do
           # a setting is one VAR=VALUE or several joined by '+'
           [ "$ev" != "-" ] && for kv in $(echo "$ev" | tr '+' ' '); do export "${kv?}"; done
-          run 300 "$OUT/envab_cur.json" python bench.py --workload "$wl" --steps 10 --warmup 2 --no-cpu-baseline
+          run 300 "$OUT/envab_cur.json" python bench.py --full --workload "$wl" --steps 10 --warmup 2 --no-cpu-baseline
           [ "$ev" != "-" ] && for kv in $(echo "$ev" | tr '+' ' '); do unset "${kv%%=*}"; done
           python3 -c "import json,sys; d=json.load(open(sys.argv[1])); k=d['step_roofline']['gpu_kernel_ms_per_step']; \
 print(f\"$ev rep$rep ms/step {d['ms_per_step']:.3f} value {d['value']:.1f} \" + ' '.join(f'{a}:{b:.3f}' for a, b in k.items()) + ' place:' + str(d.get('placement')))" \

@@ -18,6 +18,6 @@ for grp in "$@"; do
   echo "[place_diag] $(date +%T) pass $i: $ctrs"
   # shellcheck disable=SC2086
   NLS_PLACE_LOG=1 timeout -s KILL 240 rocprofv3 --pmc $ctrs --kernel-trace --output-format csv -d "$OUT/p$i" -o run -- \
-    python3 bench.py --steps 2 --warmup 0 --prof-steps 1 --no-cpu-baseline > "$OUT/p$i.log" 2>&1 || exit $?
+    python3 bench.py --steps 2 --warmup 0 --full --prof-steps 1 --no-cpu-baseline > "$OUT/p$i.log" 2>&1 || exit $?
   grep "placement" "$OUT/p$i.log"
 done
