@@ -317,6 +317,80 @@ int nls_peer_state(const nls_handle *h, int32_t *state);
 #define NLS_PLACE_MAX 8
 int nls_placement(const nls_handle *h, int32_t *n, int32_t *chosen, float *ms, uint32_t cap);
 
+/* ---- Observables --------------------------------------------------------------------
+ * Mass, energy, peak density and a non-finite check of the live field, reduced on the
+ * device by one radius-1 stencil-and-reduce pass (16 B/cell for a complex field) -- no
+ * nls_get_field round trip, and usable inside a batched nls_step(dt, n).  What the
+ * reference's users compute on the host from stored trajectories (energy_nlse.py:6-12,
+ * energy_sge.py:6-14, nlsolvers/process_h5/find_nans.py); the reference's own device
+ * energy kernel was never wired up (device/sg_solver_dev.hpp:51-80, :213-216).
+ * An additive part of ABI 6.
+ *
+ * All values are raw grid sums, with no cell volume (the 3D config has no dz): the
+ * caller scales.  L is the handle's own operator, as nls_laplacian_apply applies it
+ * (isotropic, or div(c grad) for NLS_NLSE_G2 and NLS_KG_GAUTSCHI; scale 1/(dx*dy) in 2D,
+ * 1/dx^2 in 3D).  w = m(x) for the equations that take one (nls_set_coefficients /
+ * nls_set_sg_state), else 1.
+ *
+ *   field        complex handles (NLSE family)          real handles (Gautschi family)
+ *   step         steps issued on the handle since the last nls_set_field / nls_set_sg_state
+ *                (every step of nls_step and every nls_step_sewi call counts)
+ *   mass         sum |u|^2                              sum u^2
+ *   kinetic      -Re sum conj(u) (L u)                  -sum u (L u)
+ *   p4           sum w |u|^4                            0
+ *   p6           sum w |u|^6                            0
+ *   vel2         0                                      sum v^2, v exactly what
+ *                                                       nls_get_sg_velocity(h, dt) returns
+ *   potential    energy - kinetic                       sum m G(u)
+ *   energy       see below                              vel2/2 + kinetic/2 + potential
+ *   max_abs2     max |u|^2 over the cells counted finite (0 if there is none)
+ *   nonfinite    cells with a non-finite component      cells where u or u_past is non-finite
+ *
+ * G(u): NLS_SG_GAUTSCHI, NLS_SG_G2 1 - cos u; NLS_SG_DOUBLE (1 - cos u) + 2 (1 - cos(u/2));
+ * NLS_SG_HYPERBOLIC cosh u - 1; NLS_PHI4 u^2/2 + u^4/4; NLS_KG_GAUTSCHI u^4/4.
+ *
+ * energy of the complex equations, with the signs the steppers integrate (they differ
+ * between G1 and G2):
+ *   NLS_NLSE_CUBIC   kinetic + p4/2
+ *   NLS_NLSE_CQ      kinetic + Re(sigma1) p4/2 + Re(sigma2) p6/3 -- conserved only for real
+ *                    sigma; the default sigma1 = 0.5i is not Hamiltonian
+ *   NLS_NLSE_G2      kinetic - p4/2            (SS2 and sEWI)
+ *   NLS_NLSE_CQ_G2   kinetic - s1 p4/2 - s2 p6/3
+ * No conservation is claimed for the real (wave) family: the reference's Gautschi steps
+ * evaluate the force at id_sqrt(u), and their observables are defined by value only.
+ *
+ * Non-finite cells are not excluded from the sums (IEEE decides their value).  On a
+ * multi-rank handle observing is collective (every rank calls it); mass .. energy and
+ * nonfinite are global (all-reduced, identical on every rank), while max_abs2 is the
+ * maximum over THIS RANK'S SLAB only: the transports only sum.  Records are bitwise
+ * reproducible run to run.  Observing only reads the solver state. */
+#define NLS_OBS_NFIELDS 10
+typedef struct nls_observables {
+  double step, mass, kinetic, p4, p6, vel2, potential, energy, max_abs2, nonfinite;
+} nls_observables;
+
+/* Synchronous: enqueue the pass after all work enqueued so far, wait, fill *out.  dt is
+ * used only for vel2 (real handles: dt > 0, else NLS_ERR_ARG; ignored on complex
+ * handles).  NLS_ERR_STATE without a field, or without the coefficients a step would
+ * need.  Needs no monitor ring. */
+int nls_observe(nls_handle *h, double dt, nls_observables *out);
+/* The in-stream monitor: a device ring of `capacity` records.  capacity == 0 frees the
+ * ring and turns monitoring off.  With every > 0, nls_step appends a record after each
+ * step whose count since this call is a multiple of `every` (with that step's dt); every
+ * == 0: manual records only (nls_observe_async).  Calling it again drops unread records
+ * and restarts the phase.  A monitored run's field is bit-identical to the unmonitored
+ * one.  The host counts the records: an nls_step that would append past `capacity`
+ * returns NLS_ERR_STATE ("monitor full") before enqueuing anything, with the state
+ * unchanged -- read records, then step again. */
+int nls_monitor(nls_handle *h, uint32_t every, uint32_t capacity);
+/* Append one record of the state as of all work enqueued so far; no host
+ * synchronisation (for loops that interleave nls_apply_bc or nls_step_sewi).  Needs a
+ * ring (NLS_ERR_STATE without one, or when it is full). */
+int nls_observe_async(nls_handle *h, double dt);
+/* nls_debug_oplog's convention: *n = records held; with out != NULL it also synchronises
+ * the stream, copies the oldest min(*n, cap) records into out and removes exactly those. */
+int nls_monitor_read(nls_handle *h, nls_observables *out, uint64_t cap, uint64_t *n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -48,10 +48,15 @@ struct Grid {
 // loop continues; a writer thread hands completed buffers to the callback in
 // order.  The host blocks only when the writer still holds the buffer it
 // needs (blocked_seconds() reports that time).
+// Opt-in observables (observe_capacity > 0): every push also appends one record of the
+// same state to the handle's monitor ring (nls_observe_async, no host sync); the rows, one
+// per pushed snapshot, are read with read_observables() after finish().
 template <class T> class SnapshotPipe {
  public:
   using Fn = std::function<void(uint32_t index, const T *u, uint64_t n)>;
-  SnapshotPipe(nls_handle *h, uint64_t n, Fn cb) : h_(h), n_(n), cb_(std::move(cb)) {
+  SnapshotPipe(nls_handle *h, uint64_t n, Fn cb, uint32_t observe_capacity = 0, double observe_dt = 0.0)
+      : h_(h), n_(n), cb_(std::move(cb)), observe_(observe_capacity > 0), observe_dt_(observe_dt) {
+    if (observe_) check(nls_monitor(h_, 0, observe_capacity), h_);  // manual records only
     for (auto &b : buf_) {
       void *p = nullptr;
       check(nls_host_alloc(n * sizeof(T), &p), nullptr);
@@ -83,6 +88,7 @@ template <class T> class SnapshotPipe {
     }
     hand_over_pending();  // the previous transfer is complete by now or soon
     check(nls_get_field_async(h_, reinterpret_cast<double *>(buf_[b]), n_), h_);
+    if (observe_) check(nls_observe_async(h_, observe_dt_), h_);
     pending_ = true;
     pend_index_ = index;
     pend_buf_ = b;
@@ -101,6 +107,16 @@ template <class T> class SnapshotPipe {
     rethrow();
   }
   double blocked_seconds() const { return blocked_; }
+  // the records of the pushed snapshots, in order (call after finish(); empties the ring)
+  std::vector<nls_observables> read_observables() {
+    std::vector<nls_observables> rows;
+    if (!observe_) return rows;
+    uint64_t k = 0;
+    check(nls_monitor_read(h_, nullptr, 0, &k), h_);
+    rows.resize(k);
+    if (k) check(nls_monitor_read(h_, rows.data(), k, &k), h_);
+    return rows;
+  }
 
  private:
   void hand_over_pending() {
@@ -151,6 +167,8 @@ template <class T> class SnapshotPipe {
   nls_handle *h_;
   uint64_t n_;
   Fn cb_;
+  bool observe_ = false;
+  double observe_dt_ = 0.0;
   T *buf_[2] = {nullptr, nullptr};
   bool busy_[2] = {false, false};
   int next_ = 0;
@@ -217,9 +235,10 @@ class NLSESolverDevice {
   // thread, in snapshot order; call finish() before using its results.
   NLSESolverDevice(const Grid &g, const std::complex<double> *host_u0, const Parameters &p,
                    SnapshotFn on_snapshot, int equation = NLS_NLSE_CUBIC, int device = -1,
-                   std::complex<double> s1 = {0.0, 0.5}, std::complex<double> s2 = {-0.5, 0.0})
+                   std::complex<double> s1 = {0.0, 0.5}, std::complex<double> s2 = {-0.5, 0.0},
+                   bool observe = false)
       : h_(g, equation, p.krylov_dim, device, s1, s2), p_(p), cb_(std::move(on_snapshot)),
-        pipe_(h_.get(), h_.n(), cb_) {
+        pipe_(h_.get(), h_.n(), cb_, observe ? p.num_snapshots : 0) {
     check(nls_set_field(h_.get(), reinterpret_cast<const double *>(host_u0), h_.n()), h_.get());
     // snapshot 0 = u0, taken from the device copy (bit-identical) so that its
     // file write also runs on the writer thread
@@ -234,6 +253,8 @@ class NLSESolverDevice {
       pipe_.push(stored_++);
   }
   void finish() { pipe_.finish(); }
+  // observe = true: one nls_observables row per stored snapshot (after finish())
+  std::vector<nls_observables> read_observables() { return pipe_.read_observables(); }
   // all enqueued steps and snapshot transfers complete (file writes may still run)
   void sync() {
     check(nls_sync(h_.get()), h_.get());
@@ -259,13 +280,15 @@ class SGESolverDevice {
  public:
   using SnapshotFn = std::function<void(uint32_t index, const double *u, const double *v, uint64_t n)>;
   SGESolverDevice(const Grid &g, const double *u0, const double *v0, const double *mfield, double dt,
-                  uint32_t num_snapshots, uint32_t freq, uint32_t m, SnapshotFn cb, int device = -1)
+                  uint32_t num_snapshots, uint32_t freq, uint32_t m, SnapshotFn cb, int device = -1,
+                  bool observe = false)
       : h_(g, NLS_SG_GAUTSCHI, m, device), ns_(num_snapshots), freq_(freq), cb_(std::move(cb)),
-        u_(h_.n()), v_(h_.n()) {
+        u_(h_.n()), v_(h_.n()), observe_(observe) {
     std::vector<double> up(h_.n());
     for (uint64_t i = 0; i < h_.n(); ++i) up[i] = u0[i] - dt * v0[i];  // sg_driver_dev.cpp:106
     check(nls_set_sg_state(h_.get(), u0, up.data(), mfield, h_.n()), h_.get());
     if (cb_) cb_(stored_, u0, v0, h_.n());
+    record(dt);
     ++stored_;
   }
   void step(double tau, uint32_t step_number) {
@@ -274,16 +297,28 @@ class SGESolverDevice {
       check(nls_get_field(h_.get(), u_.data(), h_.n()), h_.get());
       check(nls_get_sg_velocity(h_.get(), tau, v_.data(), h_.n()), h_.get());
       if (cb_) cb_(stored_, u_.data(), v_.data(), h_.n());
+      record(tau);
       ++stored_;
     }
   }
   uint64_t n() const { return h_.n(); }
+  // observe = true: one nls_observables row per stored snapshot (the snapshots here are
+  // synchronous reads, so is the observation)
+  const std::vector<nls_observables> &read_observables() const { return rows_; }
 
  private:
+  void record(double dt) {
+    if (!observe_) return;
+    nls_observables o;
+    check(nls_observe(h_.get(), dt, &o), h_.get());
+    rows_.push_back(o);
+  }
   Handle h_;
   uint32_t ns_, freq_;
   SnapshotFn cb_;
   std::vector<double> u_, v_;
+  bool observe_ = false;
+  std::vector<nls_observables> rows_;
   uint32_t stored_ = 0;
 };
 
@@ -377,9 +412,10 @@ class NLSESolverDevice {
   using SnapshotFn = std::function<void(uint32_t index, const std::complex<double> *u, uint64_t n)>;
 
   NLSESolverDevice(const Grid &g, const std::complex<double> *host_u0, const double *host_m,
-                   const double *host_c, const Parameters &p, SnapshotFn on_snapshot, int device = -1)
+                   const double *host_c, const Parameters &p, SnapshotFn on_snapshot, int device = -1,
+                   bool observe = false)
       : h_(g, NLS_NLSE_G2, p.krylov_dim, device), p_(p), cb_(std::move(on_snapshot)),
-        pipe_(h_.get(), h_.n(), cb_) {
+        pipe_(h_.get(), h_.n(), cb_, observe ? p.num_snapshots : 0) {
     check(nls_set_field(h_.get(), reinterpret_cast<const double *>(host_u0), h_.n()), h_.get());
     check(nls_set_coefficients(h_.get(), host_m, host_c, h_.n()), h_.get());
   }
@@ -404,6 +440,7 @@ class NLSESolverDevice {
     pipe_.push(stored_++);
   }
   void finish() { pipe_.finish(); }
+  std::vector<nls_observables> read_observables() { return pipe_.read_observables(); }
   // all enqueued steps and snapshot transfers complete (file writes may still run)
   void sync() {
     check(nls_sync(h_.get()), h_.get());
@@ -438,9 +475,10 @@ class NLSECubicQuinticSolverDevice {
   using SnapshotFn = std::function<void(uint32_t index, const std::complex<double> *u, uint64_t n)>;
 
   NLSECubicQuinticSolverDevice(const Grid &g, const std::complex<double> *host_u0, const double *host_m,
-                               const Parameters &p, SnapshotFn on_snapshot, int device = -1)
+                               const Parameters &p, SnapshotFn on_snapshot, int device = -1,
+                               bool observe = false)
       : h_(g, NLS_NLSE_CQ_G2, p.krylov_dim, device, {p.sigma1, 0.0}, {p.sigma2, 0.0}), p_(p),
-        cb_(std::move(on_snapshot)), pipe_(h_.get(), h_.n(), cb_) {
+        cb_(std::move(on_snapshot)), pipe_(h_.get(), h_.n(), cb_, observe ? p.num_snapshots : 0) {
     check(nls_set_field(h_.get(), reinterpret_cast<const double *>(host_u0), h_.n()), h_.get());
     check(nls_set_coefficients(h_.get(), host_m, nullptr, h_.n()), h_.get());
     store_snapshot();
@@ -453,6 +491,7 @@ class NLSECubicQuinticSolverDevice {
   }
   void apply_bc() { check(nls_apply_bc(h_.get()), h_.get()); }  // :75-77
   void finish() { pipe_.finish(); }
+  std::vector<nls_observables> read_observables() { return pipe_.read_observables(); }
   uint32_t snapshots_stored() const { return stored_; }
   uint64_t n() const { return h_.n(); }
 

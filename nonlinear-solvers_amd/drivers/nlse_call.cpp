@@ -20,6 +20,7 @@
 #include "cli_common.hpp"
 #include "nls_solver.hpp"
 #include "npy.hpp"
+#include "observables_out.hpp"
 
 #ifndef NLSE_EQUATION
 #define NLSE_EQUATION NLS_NLSE_CUBIC
@@ -111,6 +112,7 @@ int main(int argc, char **argv) {
       std::cerr << what << " " << std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - start).count() << " s\n";
   };
   try {
+    const char *obs_path = nls::observables_path();
     npy::Writer out = npy::Writer::open<std::complex<double>>(
         output_file, {num_snapshots, (uint64_t)ny, (uint64_t)nx});
     nls::Grid g;
@@ -125,7 +127,7 @@ int main(int argc, char **argv) {
         [&](uint32_t, const std::complex<double> *u, uint64_t n) {  // writer thread
           out.append(u, n * sizeof(std::complex<double>));
         },
-        NLSE_EQUATION, device, s1, s2);
+        NLSE_EQUATION, device, s1, s2, obs_path != nullptr);
     lap("constructed");
     for (uint32_t i = 1; i < nt; ++i) solver.step(dti, i);
     lap("enqueued");
@@ -134,6 +136,7 @@ int main(int argc, char **argv) {
     lap("synced");
     solver.finish();
     out.close();
+    if (obs_path) nls::write_observables(obs_path, solver.read_observables());
     lap("written");
   } catch (const std::exception &e) {
     std::cerr << "Error: " << e.what() << "\n";

@@ -19,6 +19,7 @@
 #include "cli_common.hpp"
 #include "nls_solver.hpp"
 #include "npy.hpp"
+#include "observables_out.hpp"
 
 static void print_usage(const char *p) {
   std::cerr << "Usage: " << p
@@ -98,6 +99,7 @@ int main(int argc, char **argv) {
       std::cerr << what << " " << std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - start).count() << " s\n";
   };
   try {
+    const char *obs_path = nls::observables_path();
     npy::Writer out = npy::Writer::open<std::complex<double>>(
         a.pos[7], {ns, (uint64_t)nz, (uint64_t)ny, (uint64_t)nx});
     nls::Grid g;
@@ -113,7 +115,7 @@ int main(int argc, char **argv) {
         [&](uint32_t, const std::complex<double> *u, uint64_t n) {  // writer thread
           out.append(u, n * sizeof(std::complex<double>));
         },
-        eq, device, s1, s2);
+        eq, device, s1, s2, obs_path != nullptr);
     lap("constructed");
     for (uint32_t i = 1; i < nt; ++i) solver.step({0.0, dt}, i);
     lap("enqueued");
@@ -122,6 +124,7 @@ int main(int argc, char **argv) {
     lap("synced");
     solver.finish();
     out.close();
+    if (obs_path) nls::write_observables(obs_path, solver.read_observables());
     lap("written");
   } catch (const std::exception &e) {
     std::cerr << "Error: " << e.what() << "\n";

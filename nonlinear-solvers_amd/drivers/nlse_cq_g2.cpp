@@ -25,6 +25,7 @@
 #include "cli_common.hpp"
 #include "nls_solver.hpp"
 #include "npy.hpp"
+#include "observables_out.hpp"
 
 namespace {
 
@@ -125,13 +126,14 @@ int main(int argc, char **argv) {
     g.ny = ny;
     g.dx = dx;
     g.dy = dy;
+    const char *obs_path = nls::observables_path();
     nls::g2::NLSECubicQuinticSolverDevice::Parameters params(ns, freq, (uint32_t)m, s1, s2);
     nls::g2::NLSECubicQuinticSolverDevice solver(
         g, u0.data(), mfield.data(), params,
         [&](uint32_t, const std::complex<double> *u, uint64_t n) {
           out.append(u, n * sizeof(std::complex<double>));
         },
-        device);
+        device, obs_path != nullptr);
     const std::complex<double> dti(0.0, dt);
     for (uint32_t i = 1; i < nt; ++i) {
       solver.step(dti, i);
@@ -139,6 +141,7 @@ int main(int argc, char **argv) {
     }
     solver.finish();
     out.close();
+    if (obs_path) nls::write_observables(obs_path, solver.read_observables());
   } catch (const std::exception &e) {
     std::cerr << "Error: " << e.what() << "\n";
     return 1;

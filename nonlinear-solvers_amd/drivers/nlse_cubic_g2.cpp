@@ -30,6 +30,7 @@
 #include "cli_common.hpp"
 #include "nls_solver.hpp"
 #include "npy.hpp"
+#include "observables_out.hpp"
 
 #ifndef G2_DIM
 #define G2_DIM 3
@@ -183,13 +184,14 @@ int main(int argc, char **argv) {
 #endif
     g.dx = dx;
     g.dy = G2_DIM == 3 ? dx : dy;
+    const char *obs_path = nls::observables_path();
     nls::g2::NLSESolverDevice::Parameters params(ns, freq, (uint32_t)m);
     nls::g2::NLSESolverDevice solver(
         g, u0.data(), mfield.data(), cfield.data(), params,
         [&](uint32_t, const std::complex<double> *u, uint64_t n) {
           out.append(u, n * sizeof(std::complex<double>));
         },
-        device);
+        device, obs_path != nullptr);
     solver.store_snapshot_online();
     const std::complex<double> dti(0.0, dt);
     for (uint32_t i = 1; i < nt; ++i) {
@@ -202,6 +204,7 @@ int main(int argc, char **argv) {
     }
     solver.finish();
     out.close();
+    if (obs_path) nls::write_observables(obs_path, solver.read_observables());
   } catch (const std::exception &e) {
     std::cerr << "Error: " << e.what() << "\n";
     return 1;

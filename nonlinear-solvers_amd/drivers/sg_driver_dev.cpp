@@ -18,6 +18,7 @@
 #include "cli_common.hpp"
 #include "nls_solver.hpp"
 #include "npy.hpp"
+#include "observables_out.hpp"
 
 int main(int argc, char **argv) {
   const cli::Args a = cli::parse(argc, argv);
@@ -67,6 +68,7 @@ int main(int argc, char **argv) {
   double io_seconds = 0.0;
   auto start = std::chrono::high_resolution_clock::now();
   try {
+    const char *obs_path = nls::observables_path();
     npy::Writer wu = npy::Writer::open<double>(prefix + "_u_device.npy", {ns, (uint64_t)nx, (uint64_t)ny});
     npy::Writer wv = npy::Writer::open<double>(prefix + "_v_device.npy", {ns, (uint64_t)nx, (uint64_t)ny});
     nls::Grid g;
@@ -83,10 +85,11 @@ int main(int argc, char **argv) {
           wv.append(v, cnt * sizeof(double));
           io_seconds += std::chrono::duration<double>(std::chrono::high_resolution_clock::now() - t0).count();
         },
-        device);
+        device, obs_path != nullptr);
     for (uint32_t i = 1; i < nt; ++i) solver.step(dt, i);
     wu.close();
     wv.close();
+    if (obs_path) nls::write_observables(obs_path, solver.read_observables());
   } catch (const std::exception &e) {
     std::cerr << "Error: " << e.what() << "\n";
     return 1;

@@ -17,7 +17,7 @@ __all__ = [
     "NLSE_CUBIC", "NLSE_CQ", "SG_GAUTSCHI", "NLSE_G2", "KG_GAUTSCHI", "SG_G2", "SG_DOUBLE", "SG_HYPERBOLIC",
     "PHI4", "NLSE_CQ_G2", "REAL_EQUATIONS", "F_EXP_ABS", "F_EXP", "F_COS_SQRT", "F_SINC_SQRT",
     "F_SINC2_SQRT", "F_ID_SQRT", "F_SINC2_HALF", "F_SINC", "MAX_KRYLOV", "NlsError", "Config", "Solver",
-    "lib", "lib_path", "rccl_unique_id", "slab_planes", "EXPORTED_SYMBOLS",
+    "lib", "lib_path", "rccl_unique_id", "slab_planes", "EXPORTED_SYMBOLS", "OBS_FIELDS", "Observables",
 ]
 
 NLSE_CUBIC, NLSE_CQ, SG_GAUTSCHI, NLSE_G2, KG_GAUTSCHI = 0, 1, 2, 3, 4
@@ -39,7 +39,10 @@ EXPORTED_SYMBOLS = (
     "nls_get_field_async", "nls_wait_field", "nls_host_alloc", "nls_host_free", "nls_slab_planes",
     "nls_step_sewi", "nls_debug_oplog", "nls_debug_knob", "nls_placement",
     "nls_peer_state", "nls_build_info",
+    "nls_observe", "nls_monitor", "nls_observe_async", "nls_monitor_read",
 )
+# the fields of one observables record (include/nls.h struct nls_observables), in order
+OBS_FIELDS = ("step", "mass", "kinetic", "p4", "p6", "vel2", "potential", "energy", "max_abs2", "nonfinite")
 # nls_debug_oplog entry kinds (include/nls.h enum nls_op_kind)
 OP_ALLREDUCE, OP_SEND, OP_RECV, OP_WAIT_HALO, OP_WAIT_COMPUTE, OP_ALLGATHER, OP_DROPPED = 1, 2, 3, 4, 5, 6, 7
 
@@ -69,6 +72,10 @@ class Timing(C.Structure):
         ("update_ms", C.c_double * MAX_KRYLOV), ("update_count", C.c_uint64 * MAX_KRYLOV),
         ("steps", C.c_uint64), ("graph_steps", C.c_uint64),
     ]
+
+
+class Observables(C.Structure):
+    _fields_ = [(n, C.c_double) for n in OBS_FIELDS]
 
 
 class NlsError(RuntimeError):
@@ -131,6 +138,10 @@ def lib():
     L.nls_build_info.argtypes = []
     L.nls_placement.argtypes = [H, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_float),
                                 C.c_uint32]
+    L.nls_observe.argtypes = [H, C.c_double, C.POINTER(Observables)]
+    L.nls_monitor.argtypes = [H, C.c_uint32, C.c_uint32]
+    L.nls_observe_async.argtypes = [H, C.c_double]
+    L.nls_monitor_read.argtypes = [H, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
     if L.nls_abi_version() != 6:
         raise RuntimeError("libnls_amd ABI mismatch")
     _LIB = L
@@ -364,6 +375,32 @@ class Solver:
         a = self._in(x)
         out = self._out()
         self._call(lib().nls_laplacian_apply, _dptr(a), _dptr(out.view(np.float64)), self.n_local)
+        return out
+
+    # -- observables (include/nls.h "Observables") -----------------------------
+    def observe(self, dt=None) -> dict:
+        """One record of the live state, reduced on the device (nls_observe; synchronous):
+        a dict over OBS_FIELDS.  Raw grid sums; real equations need dt (vel2)."""
+        o = Observables()
+        self._call(lib().nls_observe, 0.0 if dt is None else float(dt), C.byref(o))
+        return {n: getattr(o, n) for n in OBS_FIELDS}
+
+    def monitor(self, every, capacity):
+        """The in-stream monitor (nls_monitor): a device ring of `capacity` records; step()
+        appends one after every `every`-th step (0: observe_async() only; capacity 0: off)."""
+        self._call(lib().nls_monitor, int(every), int(capacity))
+
+    def observe_async(self, dt=None):
+        """Append one record to the monitor ring without a host sync (nls_observe_async)."""
+        self._call(lib().nls_observe_async, 0.0 if dt is None else float(dt))
+
+    def monitor_read(self) -> np.ndarray:
+        """The records held, oldest first, as float64 [k, 10] (columns OBS_FIELDS); removes them."""
+        n = C.c_uint64()
+        self._call(lib().nls_monitor_read, None, 0, C.byref(n))  # size only
+        out = np.empty((n.value, len(OBS_FIELDS)), np.float64)
+        if n.value:
+            self._call(lib().nls_monitor_read, out.ctypes.data_as(C.c_void_p), n.value, C.byref(n))
         return out
 
     def set_timing(self, on=True):
